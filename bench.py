@@ -1,6 +1,6 @@
 """Benchmark: points clustered/s on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         (N > 1 without a launcher: bench.py starts the N ranks below as a child process and
         relays rank 0's line; fewer than N visible GPUs: exit 2, nothing measured)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -15,6 +15,12 @@ Workloads (BASELINE.json configs, SURVEY.md §8d generator G(n, noise, dense, se
          GPU slab fits with eps halos + RCCL all-gathers of the boundary records + global
          union-find + relabel; per-GPU work fixed (weak scaling).
 A step is one pass of the hot path over the resident points (HBM in -> labels in HBM): `value`.
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config); the legs below (the per-kernel breakdown and
+roofline, end_to_end, seam, cpu_baseline) take runs of their own and are measured with --full
+only (null in a plain run's line).  --dump-outputs DIR writes what the last timed step left in
+its output arrays (dump_outputs below); the inputs are a function of the arguments alone, so two
+builds can be compared output for output.
 `end_to_end` times host SoA -> host labels on the same data (PCIe included; N = 1:
 dbscan_fit_h; N > 1: each rank's H2D of its 1/N chunk of the input, an all_to_all routing the
 points to their slabs, the node step, an all_to_all returning the labels to the chunk owners,
@@ -114,6 +120,12 @@ def parse(argv=None):
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=None,
                     help="BASELINE config shape (points per GPU, noise, dense, seed)")
     ap.add_argument("--seed", type=int, default=None, help="default 1 (N = 1), 2 (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the legs beside the headline figure: per-kernel breakdown "
+                         "and roofline, end_to_end, seam, cpu_baseline (each can still be "
+                         "switched off with its own flag below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: host_threads()")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--e2e-steps", type=int, default=3, help="end-to-end steps (0: skip)")
@@ -433,7 +445,8 @@ def main():
         k = step()
     h.sync()
     kernels, dom = {}, None
-    if not args.no_profile:
+    profiled = args.full and not args.no_profile
+    if profiled:
         # Per-kernel breakdown from a short profiled pass outside the timed region: events on
         # every launch cost ~0.2 ms per fit of extra GPU time, so the timed region
         # carries events on the dominant kernel's launches only.
@@ -473,9 +486,14 @@ def main():
     setup_ms = round(max_over_ranks(setup_s) * 1e3, 3) if node_path else None
     if isinstance(k, torch.Tensor):
         k = int(k.item())
-    prof = h.profile_read() if not args.no_profile else {}
+    prof = h.profile_read() if profiled else {}
     h.profile(False)
     stats = h.stats()
+    if args.dump_outputs:
+        if node_path:
+            dump_outputs(args.dump_outputs, *job.owned(), k, rank, world)
+        else:
+            dump_outputs(args.dump_outputs, None, cl, fl, k, 0, 1)
 
     ms_per_step = el / args.steps * 1e3
     value = n_total * args.steps / el
@@ -527,16 +545,16 @@ def main():
                     "source": pmc_src}
 
     e2e = None
-    if args.e2e_steps > 0:
+    if args.full and args.e2e_steps > 0:
         e2e = end_to_end(args, h, dist, world, rank, n_total, node_path, max_over_ranks,
                          x if not node_path else None, y if not node_path else None)
 
     seam_out = None
-    if world == 1 and not node_path and not args.no_seam:
+    if args.full and world == 1 and not node_path and not args.no_seam:
         seam_out = seam(args, h, args.cpu_threads or host_threads())
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         if world == 1 and not node_path:
             sx, sy = x.cpu().numpy(), y.cpu().numpy()
             threads = args.cpu_threads or host_threads()
@@ -570,6 +588,7 @@ def main():
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "points/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
             "value_basis": ("device-resident: coordinates already in HBM when the timed region "
                             "starts, labels left in HBM (the bench contract); the PCIe-inclusive "
@@ -609,11 +628,41 @@ def main():
                                     sorted(kernels.items(), key=lambda kv: -kv[1])},
             "kernels_ms_note": (f"per-kernel event times from {args.profile_steps} untimed "
                                 "profiled steps; the timed steps carry events only on the "
-                                "roofline kernel"),
+                                "roofline kernel" if profiled else
+                                "not measured (--full without --no-profile measures them)"),
         }
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take
+DUMP_BYTES_PER_POINT = 8 + 4 + 8  # cluster f64, flag f32, index f64 (node path only)
+
+
+def dump_outputs(path, gid, cluster, flag, n_clusters, rank, world):
+    """--dump-outputs: the arrays the last timed step left for its caller, as float .npy files.
+    One fit: cluster (f64: exact for every int32 label), flag (f32) in input order and
+    n_clusters.  Node path: this rank's owned points' labels and their global visit indices
+    (index), files suffixed _rank<r> when there are several ranks.  Outputs over the budget are
+    cut to a fixed sample: rows np.random.default_rng(0).choice(n, m, replace=False), sorted,
+    the same rows in every run with the same arguments."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = int(cluster.numel())
+    m = DUMP_BUDGET_BYTES // world // DUMP_BYTES_PER_POINT
+    arrays = {"cluster": (cluster, np.float64), "flag": (flag, np.float32)}
+    if gid is not None:
+        arrays["index"] = (gid, np.float64)
+    rows = np.sort(np.random.default_rng(0).choice(n, m, replace=False)) if n > m else None
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, (t, dt) in arrays.items():
+        a = t.cpu().numpy()
+        a = a if rows is None else a[rows]
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a.astype(dt))
+    if rank == 0:
+        np.save(os.path.join(path, "n_clusters.npy"), np.array([n_clusters], np.float64))
 
 
 def seam(args, h, threads):

@@ -28,6 +28,46 @@ def test_explicit_flags_win():
     assert (a.noise, a.seed, a.points_per_gpu) == (0.1, 7, 12_500_000)
 
 
+def test_plain_run_is_the_default():
+    """--full is off unless asked for; the legs' own switches keep their defaults under it."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert (a.full, a.dump_outputs, a.no_seam, a.no_cpu_baseline, a.e2e_steps) == \
+        (True, "d", False, False, 3)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float .npy files of the labels; over the budget the same seeded rows of
+    every array, identical from run to run."""
+    import torch
+
+    n = 1000
+    cl = torch.arange(n, dtype=torch.int32) * 2_000_000  # (labels past float32's 2^24)
+    fl = (torch.arange(n) % 3).to(torch.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), None, cl, fl, 5, 0, 1)
+    c, f = np.load(tmp_path / "a" / "cluster.npy"), np.load(tmp_path / "a" / "flag.npy")
+    assert (c.dtype, f.dtype) == (np.float64, np.float32)
+    np.testing.assert_array_equal(c, cl.numpy())
+    np.testing.assert_array_equal(f, fl.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "n_clusters.npy"), [5.0])
+
+    m = 100
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", m * bench.DUMP_BYTES_PER_POINT)
+    gid = torch.arange(n, dtype=torch.int64) + 7
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), gid, cl, fl, 5, 0, 1)
+    c, f, g = (np.load(tmp_path / "b" / f"{k}.npy") for k in ("cluster", "flag", "index"))
+    assert c.shape == f.shape == g.shape == (m,)
+    rows = (g - 7).astype(np.int64)
+    assert np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(c, cl.numpy()[rows])
+    np.testing.assert_array_equal(f, fl.numpy()[rows])
+    for k in ("cluster", "flag", "index"):
+        np.testing.assert_array_equal(np.load(tmp_path / "c" / f"{k}.npy"),
+                                      np.load(tmp_path / "b" / f"{k}.npy"))
+
+
 def test_config3_shaped_job_shards_into_slabs(tmp_path):
     """The N > 1 step on G(n, 20% noise, seed 2) (config 3's shape, scaled down) over two gloo
     ranks: every point owned once, each slab well under the whole set, labels equal one fit."""

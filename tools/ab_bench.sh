@@ -5,7 +5,7 @@
 # those kernels instead).
 set -o pipefail
 mkdir -p gpurun_out/ab
-ARGS="${BENCH_ARGS:---steps 20 --warmup 5} --no-cpu-baseline --e2e-steps 0"
+ARGS="${BENCH_ARGS:---steps 20 --warmup 5} --full --no-cpu-baseline --e2e-steps 0"
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in $VARIANTS; do
     lib=""

@@ -14,12 +14,12 @@ run() {  # name, limit, command...
   local rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/ev/$name.log; exit $rc; }
 }
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-run bench_default 400 python bench.py --steps 20 --warmup 5
-run bench_node 300 python bench.py --node --config 3 --steps 10 --warmup 3
-run bench_rccl 300 python bench.py --force-collectives --config 3 --steps 10 --warmup 3 --no-cpu-baseline
-run bench_noise 300 python bench.py --config 3 --steps 10 --warmup 3 --no-cpu-baseline --no-seam
-run bench_dense 300 python bench.py --config 4 --steps 5 --warmup 2 --no-cpu-baseline --no-seam
-run bench_big 300 python bench.py --config 5 --steps 3 --warmup 1 --no-cpu-baseline --e2e-steps 2 --no-seam
+run bench_default 400 python bench.py --full --steps 20 --warmup 5
+run bench_node 300 python bench.py --full --node --config 3 --steps 10 --warmup 3
+run bench_rccl 300 python bench.py --full --force-collectives --config 3 --steps 10 --warmup 3 --no-cpu-baseline
+run bench_noise 300 python bench.py --full --config 3 --steps 10 --warmup 3 --no-cpu-baseline --no-seam
+run bench_dense 300 python bench.py --full --config 4 --steps 5 --warmup 2 --no-cpu-baseline --no-seam
+run bench_big 300 python bench.py --full --config 5 --steps 3 --warmup 1 --no-cpu-baseline --e2e-steps 2 --no-seam
 # config 5 itself (10^9 points) through the one-process whole-node entry, phase trace on stderr
 DBSCAN_NODE_TRACE=1 run train_node_config5 400 python -u tools/train_node_probe.py 1e9 8
 run node_phase_trace 300 python -u tools/node_phase_trace.py
@@ -35,5 +35,5 @@ rm -rf gpurun_out/prof
 # box is the snapshot's; the one just written is stamped with the running sources), so the
 # committed default line carries roofline.traffic
 cp gpurun_out/ev/profiles/pmc_traffic.json profiles/pmc_traffic.json || exit 1
-run bench_default_traffic 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+run bench_default_traffic 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
 grep -h '"traffic"' gpurun_out/ev/bench_default_traffic.log | cut -c1-120 || true
