@@ -180,6 +180,8 @@ struct dbscan_handle {
     dbscan::FitStats stats;
     dbscan::SlabState slab;
     dbscan::DevBuf hx, hy, hcl, hfl;  // staging for the host-array entry points
+    dbscan::DevBuf hnr;               // ... dbscan_assign's nearest indices
+    int64_t assign_sort_min = DBSCAN_ASSIGN_SORT_DEFAULT_QUERIES;  // assigns from here: sorted
     dbscan::DevBuf boffs, hnk;        // batch fits: offsets + small-partition list; counts
     void* bpinned = nullptr;          // pinned staging of the batch tables (grow-only)
     size_t bpinned_bytes = 0;
@@ -346,6 +348,7 @@ void dbscan_destroy(dbscan_handle* h) {
     h->hy.release();
     h->hcl.release();
     h->hfl.release();
+    h->hnr.release();
     h->boffs.release();
     h->hnk.release();
     if (h->bpinned) (void)hipHostFree(h->bpinned);
@@ -1370,6 +1373,204 @@ int64_t dbscan_duplicate(const double* x, const double* y, int64_t n, const doub
         return dbscan::duplicate_points(x, y, n, rects, n_parts, eps, offsets_out, index_out,
                                         capacity);
     });
+}
+
+}  // extern "C"
+
+// ------------------------------ out-of-sample assignment --------------------------------
+
+namespace {
+
+// Arguments every assign entry point shares; false: nothing to do (m == 0).
+bool check_assign_args(const dbscan_handle* h, const dbscan_index* idx, const void* qx,
+                       const void* qy, int64_t m, const void* cluster, const void* flag) {
+    if (m < 0) throw dbscan::ArgError{"m < 0"};
+    if (m > DBSCAN_MAX_POINTS) throw dbscan::ArgError{"m exceeds DBSCAN_MAX_POINTS"};
+    if (idx->device != h->device)
+        throw dbscan::ArgError{"the handle and the index are on different devices"};
+    if (m > 0 && (!qx || !qy || !cluster || !flag)) throw dbscan::ArgError{"NULL array pointer"};
+    return m > 0;
+}
+
+int32_t index_build(dbscan_handle* h, const double* x, const double* y, const int32_t* cluster,
+                    const uint8_t* flag, int64_t n, double eps, dbscan_index** out, bool host) {
+    if (out) *out = nullptr;
+    if (!h) {
+        set_err("NULL handle");
+        return DBSCAN_EARG;
+    }
+    return guarded(h, [&]() -> int32_t {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!out) throw dbscan::ArgError{"NULL index pointer"};
+        if (n < 0) throw dbscan::ArgError{"n < 0"};
+        if (n > DBSCAN_MAX_POINTS) throw dbscan::ArgError{"n exceeds DBSCAN_MAX_POINTS"};
+        if (n > 0 && (!x || !y || !cluster || !flag)) throw dbscan::ArgError{"NULL array pointer"};
+        settle(h);
+        std::unique_ptr<dbscan_index> idx(new dbscan_index());
+        idx->device = h->device;
+        if (host && n > 0) {
+            double* dx = static_cast<double*>(h->hx.ensure(n * sizeof(double)));
+            double* dy = static_cast<double*>(h->hy.ensure(n * sizeof(double)));
+            int32_t* dcl = static_cast<int32_t*>(h->hcl.ensure(n * sizeof(int32_t)));
+            uint8_t* dfl = static_cast<uint8_t*>(h->hfl.ensure(n));
+            XferLock xl(h->device, n);
+            DBSCAN_HIP_CHECK(
+                hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            DBSCAN_HIP_CHECK(
+                hipMemcpyAsync(dy, y, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            DBSCAN_HIP_CHECK(hipMemcpyAsync(dcl, cluster, n * sizeof(int32_t),
+                                            hipMemcpyHostToDevice, h->stream));
+            DBSCAN_HIP_CHECK(hipMemcpyAsync(dfl, flag, n, hipMemcpyHostToDevice, h->stream));
+            DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+            x = dx;
+            y = dy;
+            cluster = dcl;
+            flag = dfl;
+        }
+        try {
+            dbscan::build_index(h->stream, h->ws, &h->prof, x, y, cluster, flag, n, eps,
+                                idx.get());
+        } catch (...) {
+            (void)hipStreamSynchronize(h->stream);  // nothing of a failed build stays queued
+            throw;
+        }
+        DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof.flush();
+        *out = idx.release();
+        return DBSCAN_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t dbscan_index_build_device(dbscan_handle* h, const double* d_x, const double* d_y,
+                                  const int32_t* d_cluster, const uint8_t* d_flag, int64_t n,
+                                  double eps, dbscan_index** out) {
+    return index_build(h, d_x, d_y, d_cluster, d_flag, n, eps, out, false);
+}
+
+int32_t dbscan_index_build(dbscan_handle* h, const double* x, const double* y,
+                           const int32_t* cluster, const uint8_t* flag, int64_t n, double eps,
+                           dbscan_index** out) {
+    return index_build(h, x, y, cluster, flag, n, eps, out, true);
+}
+
+// Frees memory only: no launch, no stream work (the caller has synchronized every handle with
+// an assign queued on the index).
+void dbscan_index_destroy(dbscan_index* idx) {
+    if (!idx) return;
+    int cur = -1;
+    const int dev = idx->device;
+    const bool moved = hipGetDevice(&cur) == hipSuccess && cur != dev &&
+                       hipSetDevice(dev) == hipSuccess;
+    delete idx;
+    if (moved) (void)hipSetDevice(cur);
+}
+
+int32_t dbscan_index_stats(const dbscan_index* idx, int64_t* out, int32_t max) {
+    if (!idx || !out || max < 0) {
+        set_err(!idx ? "NULL index" : "NULL output pointer");
+        return DBSCAN_EARG;
+    }
+    const int64_t v[8] = {idx->n,    idx->ncores, idx->max_cluster, idx->ncells,
+                          idx->mode == 0 ? idx->g.nx : 0, idx->mode == 0 ? idx->g.ny : 0,
+                          idx->mode, idx->device};
+    const int k = std::min<int32_t>(max, 8);
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+int32_t dbscan_assign_device_async(dbscan_handle* h, const dbscan_index* idx, const double* d_qx,
+                                   const double* d_qy, int64_t m, int32_t* d_cluster,
+                                   uint8_t* d_flag, int32_t* d_nearest) {
+    if (!h || !idx) {
+        set_err(!h ? "NULL handle" : "NULL index");
+        return DBSCAN_EARG;
+    }
+    return guarded(h, [&]() -> int32_t {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!check_assign_args(h, idx, d_qx, d_qy, m, d_cluster, d_flag)) return DBSCAN_OK;
+        if (h->prof.pending.size() > 4096) h->prof.flush_ready();  // bound the event backlog
+        dbscan::enqueue_assign(h->stream, h->ws, &h->prof, idx, d_qx, d_qy, m, d_cluster, d_flag,
+                               d_nearest, h->assign_sort_min);
+        return DBSCAN_OK;
+    });
+}
+
+int32_t dbscan_assign_device(dbscan_handle* h, const dbscan_index* idx, const double* d_qx,
+                             const double* d_qy, int64_t m, int32_t* d_cluster, uint8_t* d_flag,
+                             int32_t* d_nearest) {
+    if (!h || !idx) {
+        set_err(!h ? "NULL handle" : "NULL index");
+        return DBSCAN_EARG;
+    }
+    return guarded(h, [&]() -> int32_t {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!check_assign_args(h, idx, d_qx, d_qy, m, d_cluster, d_flag)) return DBSCAN_OK;
+        settle(h);
+        dbscan::enqueue_assign(h->stream, h->ws, &h->prof, idx, d_qx, d_qy, m, d_cluster, d_flag,
+                               d_nearest, h->assign_sort_min);
+        DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->prof.flush();
+        return DBSCAN_OK;
+    });
+}
+
+int32_t dbscan_assign(dbscan_handle* h, const dbscan_index* idx, const double* qx,
+                      const double* qy, int64_t m, int32_t* cluster_out, uint8_t* flag_out,
+                      int32_t* nearest_out) {
+    if (!h || !idx) {
+        set_err(!h ? "NULL handle" : "NULL index");
+        return DBSCAN_EARG;
+    }
+    return guarded(h, [&]() -> int32_t {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!check_assign_args(h, idx, qx, qy, m, cluster_out, flag_out)) return DBSCAN_OK;
+        settle(h);
+        double* dx = static_cast<double*>(h->hx.ensure(m * sizeof(double)));
+        double* dy = static_cast<double*>(h->hy.ensure(m * sizeof(double)));
+        int32_t* dcl = static_cast<int32_t*>(h->hcl.ensure(m * sizeof(int32_t)));
+        uint8_t* dfl = static_cast<uint8_t*>(h->hfl.ensure(m));
+        int32_t* dnr = nearest_out
+                           ? static_cast<int32_t*>(h->hnr.ensure(m * sizeof(int32_t)))
+                           : nullptr;
+        {
+            XferLock xl(h->device, m);
+            DBSCAN_HIP_CHECK(
+                hipMemcpyAsync(dx, qx, m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            DBSCAN_HIP_CHECK(
+                hipMemcpyAsync(dy, qy, m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            if (xl.held()) DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        dbscan::enqueue_assign(h->stream, h->ws, &h->prof, idx, dx, dy, m, dcl, dfl, dnr,
+                               h->assign_sort_min);
+        DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+        {
+            XferLock xl(h->device, m);
+            DBSCAN_HIP_CHECK(hipMemcpyAsync(cluster_out, dcl, m * sizeof(int32_t),
+                                            hipMemcpyDeviceToHost, h->stream));
+            DBSCAN_HIP_CHECK(hipMemcpyAsync(flag_out, dfl, m, hipMemcpyDeviceToHost, h->stream));
+            if (dnr)
+                DBSCAN_HIP_CHECK(hipMemcpyAsync(nearest_out, dnr, m * sizeof(int32_t),
+                                                hipMemcpyDeviceToHost, h->stream));
+            DBSCAN_HIP_CHECK(hipStreamSynchronize(h->stream));
+        }
+        h->prof.flush();
+        return DBSCAN_OK;
+    });
+}
+
+int64_t dbscan_set_assign_sort_min(dbscan_handle* h, int64_t min_queries) {
+    if (!h || min_queries < 0) {
+        set_err(!h ? "NULL handle" : "min_queries < 0");
+        return DBSCAN_EARG;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int64_t old = h->assign_sort_min;
+    h->assign_sort_min = min_queries;
+    return old;
 }
 
 int32_t dbscan_generate_blobs_device(dbscan_handle* h, double* d_x, double* d_y, int64_t n,

@@ -178,7 +178,11 @@ struct Workspace {
         is_root, rank, misc, qidx, qkey, qstart, qrep, qmask, blockcnt, heads, tkey, tstart, tmap,
         tslot, qcomp, nbr, tq, tnb, tstage, inv, packed, slab_lor, own_flag, bigt, zs, tclass, tsz,
         key3, perm3, lroots, box_edges, box_map, tcore, tpart, pbox, ptab, shm, route, route_tab,
-        spread, band;
+        spread, band,
+        // out-of-sample assignment (assign.hip): query sort keys / order and index-build scratch;
+        // nothing a fit reads or writes
+        a_key, a_key2, a_key3, a_val, a_val2, a_val3, a_hist, a_tmp, a_cx, a_cy, a_cl, a_id,
+        a_misc;
     bool spread_ready = false;  // spread.p holds zeroed barrier words (small.hip)
     double* stats_host = nullptr;  // pinned: the stats block read_fit_stats copies back
     bool fit_mirrored = false;     // the last fit (an LDS form) wrote its stats into fit_block
@@ -226,6 +230,7 @@ struct Workspace {
         if (ring_host) (void)hipHostFree(ring_host);
     }
     ScanState scan;
+    ScanState ascan;    // the assignment's scans and sorts (assign.hip): its own look-back words
     BucketSort bucket;  // the bucketed sort's buffers (large fits only)
     int64_t fit_n = 0;               // the last enqueued fit
     int fit_mode = 0;
@@ -233,6 +238,7 @@ struct Workspace {
     uint32_t* key_sorted = nullptr;  // key or key2, likewise
     void release() {
         scan.buf.release();
+        ascan.buf.release();
         bucket.release();
         for (DevBuf* b : {&key, &key2, &perm, &perm2, &hist, &scan_tmp, &xy, &cell, &ckey, &cstart,
                           &seg, &core, &parent, &lab, &is_root, &rank, &misc, &qidx, &qkey,
@@ -240,7 +246,9 @@ struct Workspace {
                           &qcomp, &nbr, &tq, &tnb, &tstage, &inv, &packed, &slab_lor,
                           &own_flag, &bigt, &zs, &tclass, &tsz, &key3, &perm3, &lroots,
                           &box_edges, &box_map, &tcore, &tpart, &pbox, &ptab, &shm, &route,
-                          &route_tab, &spread, &band})
+                          &route_tab, &spread, &band, &a_key, &a_key2, &a_key3, &a_val,
+                          &a_val2, &a_val3, &a_hist, &a_tmp, &a_cx, &a_cy, &a_cl, &a_id,
+                          &a_misc})
             b->release();
         spread_ready = false;
         band_ready = false;
@@ -557,4 +565,45 @@ int bbox_partials(hipStream_t s, const double* x, const double* y, int64_t n, De
 void scan3(hipStream_t s, const int32_t* in, int64_t n, int64_t stride, int32_t* out,
            int32_t* t0, int32_t* t1, int32_t* t2);
 
+
+// ---- out-of-sample assignment (assign.hip) ----
+// The index grid: cell(v) = floor((v * 0.5 - vmin2) * inv2) per axis, one side >= eps for both
+// axes, nx x ny cells in ntx x nty tiles of 8x8 cells.
+struct AssignGrid {
+    double xmin2, ymin2, inv2;
+    int32_t nx, ny, ntx, nty;
+};
+// One tile of the dense tile map: bit l of mask = local cell l (row << 3 | column) holds cores;
+// base = the occupied-cell ordinal of the tile's first occupied cell, so local cell l is
+// occupied cell base + popcount(mask below bit l).
+struct AssignTile {
+    uint64_t mask;
+    int32_t base;
+    int32_t pad;
+};
+constexpr int64_t kAssignMaxTiles = int64_t(1) << 20;  // the cell budget: a 16 MB tile map
+// Builds an index over the cores of a fitted model (synchronous: returns after the stream has
+// drained); enqueue_assign queues one batch of queries against it.  sort_min: batches of at
+// least this many queries are binned and sorted on the index grid first.
+void build_index(hipStream_t s, Workspace& ws, Profiler* prof, const double* x, const double* y,
+                 const int32_t* cluster, const uint8_t* flag, int64_t n, double eps,
+                 dbscan_index* idx);
+void enqueue_assign(hipStream_t s, Workspace& ws, Profiler* prof, const dbscan_index* idx,
+                    const double* qx, const double* qy, int64_t m, int32_t* cluster,
+                    uint8_t* flag, int32_t* nearest, int64_t sort_min);
+
 }  // namespace dbscan
+
+// A core-point index (dbscan_index_build*): owns its device buffers, read-only once built.
+// Cores sorted by cell key (tile << 6 | local cell) as AoS records xy[k] = (x, y) and
+// ci[k] = (cluster, input index); cstart[c] = first record of occupied cell c (ncells + 1
+// entries); tmap[ntx * nty] the tile map.  All-pairs mode keeps the records in input order and
+// has no grid.
+struct dbscan_index {
+    int device = 0;
+    int mode = 2;  // 0 grid, 1 all pairs, 2 no pairs
+    int64_t n = 0, ncores = 0, max_cluster = 0, ncells = 0;
+    double eps2 = 0.0;
+    dbscan::AssignGrid g{};
+    dbscan::DevBuf xy, ci, cstart, tmap, bits;
+};

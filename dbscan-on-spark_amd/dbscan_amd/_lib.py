@@ -83,6 +83,14 @@ SIGNATURES = [
     ("dbscan_owned_rows_device", _i64, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64]),
     ("dbscan_rows_unpack_device", _i64, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("dbscan_label_scatter_device", _i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    ("dbscan_index_build_device", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _d, _vp]),
+    ("dbscan_index_build", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _d, _vp]),
+    ("dbscan_index_destroy", None, [_vp]),
+    ("dbscan_index_stats", _i32, [_vp, _vp, _i32]),
+    ("dbscan_assign_device_async", _i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("dbscan_assign_device", _i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("dbscan_assign", _i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("dbscan_set_assign_sort_min", _i64, [_vp, _i64]),
 ]
 SMALL_MAX_POINTS = 8192  # DBSCAN_SMALL_MAX_POINTS
 
@@ -206,6 +214,14 @@ class Handle:
         """Test hook: the spread fit's barrier poll bound (0: every barrier gives up at once and
         the fit is re-run by the one-workgroup kernel).  Returns the previous bound."""
         r = load().dbscan_set_spread_spin_limit(self._h, int(polls))
+        if r < 0:
+            check(int(r))
+        return int(r)
+
+    def set_assign_sort_min(self, min_queries: int) -> int:
+        """Assigns of >= min_queries queries are binned and sorted on the index grid first
+        (assign.hip; 0: every batch, 1 << 40: none).  Returns the previous value."""
+        r = load().dbscan_set_assign_sort_min(self._h, int(min_queries))
         if r < 0:
             check(int(r))
         return int(r)

@@ -80,6 +80,92 @@ def fit_batch_tensors_async(x: torch.Tensor, y: torch.Tensor, offsets, eps: floa
         float(eps), int(min_points), int(mode), _p(cluster), _p(flag), _p(n_clusters)))
 
 
+def _check_tensor(name: str, t, dtype, device, numel=None) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: a torch tensor is required")
+    if not (t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.dtype == dtype):
+        raise ValueError(f"{name}: contiguous 1-D {dtype} device tensor required")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: on {t.device}, expected {device}")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: {t.numel()} values, expected {numel}")
+
+
+def build_index_tensors(x: torch.Tensor, y: torch.Tensor, cluster: torch.Tensor,
+                        flag: torch.Tensor, eps: float, handle: _lib.Handle):
+    """A ClusterIndex over a model held in device tensors (float64 x / y, int32 cluster, uint8
+    flag; dbscan_index_build_device).  Synchronous; the index copies what it needs, so the
+    tensors may be freed afterwards."""
+    from .assign import ClusterIndex
+
+    if not isinstance(handle, _lib.Handle):
+        raise ValueError("handle: a dbscan_amd.Handle is required")
+    _check_tensor("x", x, torch.float64, None)
+    n = x.numel()
+    if x.device.index != handle.device:
+        raise ValueError(f"x: on {x.device}, the handle is on device {handle.device}")
+    _check_tensor("y", y, torch.float64, x.device, n)
+    _check_tensor("cluster", cluster, torch.int32, x.device, n)
+    _check_tensor("flag", flag, torch.uint8, x.device, n)
+    torch.cuda.current_stream(x.device).synchronize()
+    out = ctypes.c_void_p()
+    _lib.check(_lib.load().dbscan_index_build_device(handle.ptr, _p(x), _p(y), _p(cluster),
+                                                     _p(flag), n, float(eps), ctypes.byref(out)))
+    return ClusterIndex._from_ptr(out, handle, float(eps))
+
+
+def _assign_args(index, qx, qy, handle, cluster, flag, nearest):
+    from .assign import ClusterIndex
+
+    if not isinstance(index, ClusterIndex):
+        raise ValueError("index: a ClusterIndex is required")
+    if not isinstance(handle, _lib.Handle):
+        raise ValueError("handle: a dbscan_amd.Handle is required")
+    _check_tensor("qx", qx, torch.float64, None)
+    m = qx.numel()
+    if qx.device.index != handle.device:
+        raise ValueError(f"qx: on {qx.device}, the handle is on device {handle.device}")
+    _check_tensor("qy", qy, torch.float64, qx.device, m)
+    _check_tensor("cluster", cluster, torch.int32, qx.device, m)
+    _check_tensor("flag", flag, torch.uint8, qx.device, m)
+    if nearest is not None:
+        _check_tensor("nearest", nearest, torch.int32, qx.device, m)
+    return m
+
+
+def assign_tensors(index, qx: torch.Tensor, qy: torch.Tensor, handle: _lib.Handle,
+                   cluster: torch.Tensor = None, flag: torch.Tensor = None,
+                   nearest: torch.Tensor = None, want_nearest: bool = False):
+    """Assign device float64 queries against a ClusterIndex (dbscan_assign_device; returns after
+    the handle's stream has drained): (cluster int32, flag uint8, nearest int32 or None) in
+    query order.  The caller's pending torch work on qx/qy is synchronized first."""
+    if isinstance(qx, torch.Tensor) and qx.is_cuda:
+        if cluster is None:
+            cluster = torch.empty(qx.numel(), dtype=torch.int32, device=qx.device)
+        if flag is None:
+            flag = torch.empty(qx.numel(), dtype=torch.uint8, device=qx.device)
+        if nearest is None and want_nearest:
+            nearest = torch.empty(qx.numel(), dtype=torch.int32, device=qx.device)
+    m = _assign_args(index, qx, qy, handle, cluster, flag, nearest)
+    torch.cuda.current_stream(qx.device).synchronize()
+    _lib.check(_lib.load().dbscan_assign_device(
+        handle.ptr, index.ptr, _p(qx), _p(qy), m, _p(cluster), _p(flag),
+        _p(nearest) if nearest is not None else None))
+    return cluster, flag, nearest
+
+
+def assign_tensors_async(index, qx: torch.Tensor, qy: torch.Tensor, handle: _lib.Handle,
+                         cluster: torch.Tensor, flag: torch.Tensor,
+                         nearest: torch.Tensor = None) -> None:
+    """Enqueue an assign on the handle's stream and return at once
+    (dbscan_assign_device_async); handle.sync() before reading the outputs, and before the
+    index is closed.  qx/qy must not be written by other streams until then."""
+    m = _assign_args(index, qx, qy, handle, cluster, flag, nearest)
+    _lib.check(_lib.load().dbscan_assign_device_async(
+        handle.ptr, index.ptr, _p(qx), _p(qy), m, _p(cluster), _p(flag),
+        _p(nearest) if nearest is not None else None))
+
+
 def generate_blobs(n: int, noise: float, dense: float, seed: int, handle: _lib.Handle,
                    device=None):
     """SURVEY §8d generator on the device (no PCIe): returns (x, y) float64 tensors."""

@@ -13,6 +13,8 @@ the reference's whole-job API, over libdbscan_hip.so.
                   permutation of them: DBSCANSuite maps them through `corresponding`).
   cluster, flag   the same labels as numpy arrays (no per-point objects)
   predict(v)      NotImplementedError, as in the reference (DBSCAN.scala:300-302)
+  assign(data)    out-of-sample assignment (not in the reference): the labels new points get from
+                  the model's cores under the Archery border rule; index() is its ClusterIndex
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ from typing import Iterable, List, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from .assign import ClusterIndex
 from .local import DBSCANLabeledPoint, DBSCANPoint, Flag, train_node
 from .partition import DBSCANRectangle, partition_points
 
@@ -52,6 +55,7 @@ class DBSCAN:
         self.n_clusters = n_clusters
         self._data = data
         self._labeled = None
+        self._index = None
 
     @staticmethod
     def train(data, eps: float, minPoints: int, maxPointsPerPartition: int,
@@ -86,3 +90,18 @@ class DBSCAN:
 
     def predict(self, vector) -> DBSCANLabeledPoint:  # DBSCAN.scala:300-302
         raise NotImplementedError("DBSCAN.predict is not implemented (as in the reference)")
+
+    def index(self, handle: Optional[_lib.Handle] = None) -> ClusterIndex:
+        """The model's core-point index (assign.ClusterIndex), built on first use and kept."""
+        if self._index is None:
+            x, y, _ = _as_xy(self._data)
+            self._index = ClusterIndex(x, y, self.cluster, self.flag, self.eps, handle)
+        return self._index
+
+    def assign(self, data) -> Tuple[np.ndarray, np.ndarray]:
+        """Out-of-sample assignment of new points (the same forms of `data` as train takes):
+        (cluster int32, flag uint8) in input order -- each point Border of the first-opened
+        cluster with a core within eps of it (the Archery border rule), else Noise with
+        cluster 0."""
+        qx, qy, _ = _as_xy(data)
+        return self.index().assign(qx, qy)

@@ -441,6 +441,69 @@ int32_t dbscan_label_scatter_device(dbscan_handle* h, const int64_t* d_rows, int
                                     int64_t start, int64_t m, int32_t* d_cluster,
                                     uint8_t* d_flag);
 
+/* ---------------------------------------------------------------------------------------
+ * Out-of-sample assignment: which cluster does a new point belong to?  (The reference names
+ * the operation, DBSCAN.predict at DBSCAN.scala:300-302, and leaves it unimplemented.)
+ * A model is the result of any full fit in mode NAIVE or ARCHERY -- x, y, cluster, flag of n
+ * points plus eps; both modes give the same cores and numbering.  Its cores are the points
+ * with flag == DBSCAN_FLAG_CORE.  For a query q, C(q) = the cores c with
+ *     dx = c.x - q.x; dy = c.y - q.y; dx*dx + dy*dy <= eps*eps      (fp64, never fused: the
+ *                                                     predicate of DBSCANPoint.scala:26-30)
+ *   cluster(q) = the smallest cluster[c] over C(q) -- the first-opened adjacent cluster, the
+ *                label the ARCHERY border rule above gives a non-core point at q; 0 if C(q)
+ *                is empty
+ *   flag(q)    = DBSCAN_FLAG_BORDER if C(q) is not empty, else DBSCAN_FLAG_NOISE (never Core:
+ *                a query is not part of the fit)
+ *   nearest(q) = the model input index of the core of C(q) with the smallest d2, ties to the
+ *                smallest input index; -1 if C(q) is empty            (optional output)
+ * Non-finite values follow the predicate literally, as for fits: with a finite eps*eps a
+ * non-finite query or core (minPoints <= 0 models have them) is nobody's neighbour;
+ * eps*eps = +inf matches every pair whose d2 is not NaN (an all-pairs kernel, O(m * cores));
+ * eps*eps = NaN matches nothing.  eps*eps is computed once: a negative eps acts like |eps|.
+ * Models fitted in DBSCAN_MODE_ARCHERY_F32BOX are out of scope (their neighbour relation is
+ * directed); nothing detects them.
+ *
+ * dbscan_index_build*: compacts the cores, lays a uniform grid (side >= eps, coarsened until it
+ *   fits a fixed cell budget -- a wide sparse model never fails) over their bounding box and
+ *   sorts them by cell.  Synchronous; settles a pending asynchronous fit first.  A core with
+ *   cluster <= 0 is DBSCAN_EARG.  The index owns device buffers of its own: later fits on the
+ *   handle leave it intact, it is read-only once built, and several handles (of the index's
+ *   device), each on its own thread, may assign from it at once.
+ * dbscan_index_destroy: frees the buffers; launches nothing and waits for nothing, so the
+ *   caller must dbscan_sync every handle with a queued assign on the index first.
+ * dbscan_index_stats: [0] n  [1] cores indexed  [2] largest cluster id  [3] occupied cells
+ *   [4] nx  [5] ny  [6] grid mode (0 grid, 1 all pairs, 2 no pairs)  [7] device.  Returns the
+ *   number of values written (<= max).
+ * dbscan_assign_device_async: enqueues the assignment of m queries (device arrays) on the
+ *   handle's stream and returns; outputs in query order, d_nearest may be NULL.  It touches
+ *   none of a fit's state, so fits and assigns queued on one handle do not disturb each other.
+ *   dbscan_assign_device returns after the stream has drained; dbscan_assign takes host arrays.
+ *   n == 0 and m == 0 are DBSCAN_OK.
+ * Batches of at least dbscan_set_assign_sort_min(h, ...) queries (default
+ * DBSCAN_ASSIGN_SORT_DEFAULT_QUERIES) are binned and sorted on the index grid first, so the 64
+ * lanes of a wave walk the same few cells; smaller batches look their cells up in query order.
+ * Same results bit for bit.  Returns the previous value. */
+typedef struct dbscan_index dbscan_index;
+int32_t dbscan_index_build_device(dbscan_handle* h, const double* d_x, const double* d_y,
+                                  const int32_t* d_cluster, const uint8_t* d_flag, int64_t n,
+                                  double eps, dbscan_index** out);
+int32_t dbscan_index_build(dbscan_handle* h, const double* x, const double* y,
+                           const int32_t* cluster, const uint8_t* flag, int64_t n, double eps,
+                           dbscan_index** out);
+void dbscan_index_destroy(dbscan_index* idx);
+int32_t dbscan_index_stats(const dbscan_index* idx, int64_t* out, int32_t max);
+int32_t dbscan_assign_device_async(dbscan_handle* h, const dbscan_index* idx, const double* d_qx,
+                                   const double* d_qy, int64_t m, int32_t* d_cluster,
+                                   uint8_t* d_flag, int32_t* d_nearest);
+int32_t dbscan_assign_device(dbscan_handle* h, const dbscan_index* idx, const double* d_qx,
+                             const double* d_qy, int64_t m, int32_t* d_cluster, uint8_t* d_flag,
+                             int32_t* d_nearest);
+int32_t dbscan_assign(dbscan_handle* h, const dbscan_index* idx, const double* qx,
+                      const double* qy, int64_t m, int32_t* cluster_out, uint8_t* flag_out,
+                      int32_t* nearest_out);
+#define DBSCAN_ASSIGN_SORT_DEFAULT_QUERIES 1048576
+int64_t dbscan_set_assign_sort_min(dbscan_handle* h, int64_t min_queries);
+
 /* Device-side synthetic generator G(n, noise, dense, seed) of SURVEY.md §8d (32 isotropic
  * Gaussian blobs, splitmix64 + Box-Muller, uniform noise), then a seeded shuffle of the
  * visit order.  Writes d_x, d_y (device).  Used by bench.py so 10^7..10^9 points need no PCIe. */

@@ -8,6 +8,7 @@
 //   LocalDBSCANArchery   LocalDBSCANArchery.scala:32-126 (float32 search box: mode 2)
 //   DBSCANRectangle      DBSCANRectangle.scala:23-53
 //   DBSCAN::train        DBSCAN.scala:40-48,72-283: labeledPoints (input order) + partitions
+//   DBSCAN::assign       (not in the reference) out-of-sample assignment of new points
 // A vector with fewer than two coordinates throws std::out_of_range (the reference's
 // IndexOutOfBounds from vector(1)); HIP failures throw std::runtime_error with
 // dbscan_last_error().  There is no CPU fallback.
@@ -283,6 +284,54 @@ class DBSCAN {
     DBSCANLabeledPoint predict(const std::vector<double>&) const {  // DBSCAN.scala:300-302
         throw std::logic_error("DBSCAN.predict is not implemented (as in the reference)");
     }
+    // Out-of-sample assignment (not in the reference; dbscan_index_build / dbscan_assign): each
+    // new point becomes Border of the first-opened cluster with a core within eps of it -- the
+    // label the Archery border rule gives a non-core point there -- else Noise with cluster
+    // Unknown.  Input order; the core-point index is built on first use and kept.
+    std::vector<DBSCANLabeledPoint> assign(const std::vector<DBSCANPoint>& points) const {
+        if (!index_) {
+            const int64_t n = (int64_t)labeled_.size();
+            std::vector<double> xs((size_t)n), ys((size_t)n);
+            std::vector<int32_t> cl((size_t)n);
+            std::vector<uint8_t> fl((size_t)n);
+            for (int64_t i = 0; i < n; ++i) {
+                xs[(size_t)i] = labeled_[(size_t)i].x();
+                ys[(size_t)i] = labeled_[(size_t)i].y();
+                cl[(size_t)i] = labeled_[(size_t)i].cluster;
+                fl[(size_t)i] = static_cast<uint8_t>(labeled_[(size_t)i].flag);
+            }
+            std::shared_ptr<Handle> h(new Handle(0));
+            dbscan_index* raw = nullptr;
+            if (dbscan_index_build(h->get(), xs.data(), ys.data(), cl.data(), fl.data(), n, eps,
+                                   &raw) != DBSCAN_OK)
+                throw std::runtime_error(std::string("dbscan_index_build: ") +
+                                         dbscan_last_error());
+            // (every assign below is synchronous, so nothing is queued when the index goes)
+            index_.reset(raw, dbscan_index_destroy);
+            indexHandle_ = h;
+        }
+        const int64_t m = (int64_t)points.size();
+        std::vector<double> qx((size_t)m), qy((size_t)m);
+        for (int64_t i = 0; i < m; ++i) {
+            qx[(size_t)i] = points[(size_t)i].x();
+            qy[(size_t)i] = points[(size_t)i].y();
+        }
+        std::vector<int32_t> cl((size_t)m);
+        std::vector<uint8_t> fl((size_t)m);
+        if (dbscan_assign(indexHandle_->get(), index_.get(), qx.data(), qy.data(), m, cl.data(),
+                          fl.data(), nullptr) != DBSCAN_OK)
+            throw std::runtime_error(std::string("dbscan_assign: ") + dbscan_last_error());
+        std::vector<DBSCANLabeledPoint> out;
+        out.reserve((size_t)m);
+        for (int64_t i = 0; i < m; ++i) {
+            DBSCANLabeledPoint lp(points[(size_t)i]);
+            lp.cluster = cl[(size_t)i];
+            lp.flag = static_cast<Flag>(fl[(size_t)i]);
+            lp.visited = true;
+            out.push_back(std::move(lp));
+        }
+        return out;
+    }
     const double eps;
     const int minPoints;
     const int maxPointsPerPartition;
@@ -292,6 +341,8 @@ class DBSCAN {
     std::vector<DBSCANLabeledPoint> labeled_;
     std::vector<std::pair<int, DBSCANRectangle>> partitions_;
     int64_t nClusters_ = 0;
+    mutable std::shared_ptr<Handle> indexHandle_;  // assign(): the handle the index was built on
+    mutable std::shared_ptr<dbscan_index> index_;  // ... and the index (shared by copies)
 };
 
 }  // namespace dbscan
